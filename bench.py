@@ -2,7 +2,7 @@
 """bench.py - images/sec of the extract hot path (features + eigs) on MI355X, with the kernel roofline
 and a CPU baseline (the oracle, i.e. the reference's numpy/scipy/torch-CPU path) timed beside it.
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR]
 
 ``--gpus N`` with N > 1 launches itself as N ranks (``python -m torch.distributed.run --nproc-per-node N``, one process
 per GPU over RCCL) unless it already runs under such a launcher (WORLD_SIZE set); the line reports ``ranks_seen``.
@@ -134,10 +134,19 @@ def parse():
     ap.add_argument("--tail-overlap", default="auto", choices=["auto", "on", "off"],
                     help="spectral stage of all forwards but the last on a side stream under the last forward (auto: only for a "
                          "one-step --dataset shard, where the step's tail is exposed; in the steady state it measured slower)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the run, write what the timed path delivered to the host in its LAST step (rank 0): "
+                         "DIR/eigenvalues.npy [n, K] and DIR/eigenvectors.npy [n, K, N], float32, row i of both the same "
+                         "image; at most 64 MB in all, so n is a fixed seeded sample of the step's images when the step is "
+                         "larger.  The timed region starts at the same image whatever the warm-up ran, so two builds run "
+                         "with the same arguments can be compared output for output")
     ap.add_argument("--overlap", action="store_true",
                     help="run the spectral stage of sub-batch i on a side stream under the ViT of sub-batch i+1 "
                          "(measured slower on MI355X: both stages are bandwidth-bound; default off)")
-    return ap.parse_args()
+    a = ap.parse_args()
+    if a.steps < 1 and a.dataset <= 0:
+        ap.error("--steps must be at least 1")
+    return a
 
 
 def spawn_ranks_if_needed(a):
@@ -325,6 +334,21 @@ def chunk_counts(cnt: int, vit_batch: int, lead: bool = False, round_images: flo
         return [cnt - sum(sizes)] + sizes
     sizes[-1] = cnt - sum(sizes[:-1])
     return sizes
+
+
+DUMP_BYTES = 64 * 10 ** 6 - 4096    # --dump-outputs: the arrays' bytes, leaving room for the two .npy headers
+
+
+def last_step_outputs(block: torch.Tensor, K: int, n_patches: int):
+    """--dump-outputs: ``block`` is one step's results as the host receives them (row = one image: the ``K * n_patches``
+    eigenvector values, then the ``K`` eigenvalues; distributed.pack_records) -> ``{"eigenvalues": [n, K],
+    "eigenvectors": [n, K, N]}`` float32, ``n`` = every image, or a seeded sample in step order when they exceed DUMP_BYTES."""
+    rows = block.shape[0]
+    n = min(rows, DUMP_BYTES // (block.shape[1] * 4))
+    pick = np.arange(rows) if n == rows else np.sort(np.random.default_rng(0).choice(rows, n, replace=False))
+    sel = block[torch.from_numpy(pick)].numpy()
+    return {"eigenvalues": np.ascontiguousarray(sel[:, K * n_patches:]),
+            "eigenvectors": np.ascontiguousarray(sel[:, :K * n_patches]).reshape(n, K, n_patches)}
 
 
 _TAIL = {}
@@ -656,6 +680,8 @@ def run_steps(model, feeder, counts, a, rank, world, n_patches, w_dtype, first_c
                                          for s_, st_, n_, b_, e_ in d2h_log[-3:]],
                           "h2d_copies": [] if feeder.resident else
                           [[c_, n_, round(ev_start.elapsed_time(b_), 3), round(ev_start.elapsed_time(r_), 3)] for c_, n_, b_, r_ in feeder.log[:12]]}
+    run_steps.last_outputs = (last_step_outputs(host_out[(len(counts) - 1) % n_ring, :counts[-1]], a.K, n_patches)
+                              if a.dump_outputs and rank == 0 else None)
     return elapsed, host_enqueue_s, infos, gathered, chunk
 
 
@@ -669,6 +695,8 @@ def main():
     backend = torch.distributed.get_backend() if world > 1 else None
     if world > 1 and backend != "nccl" and not os.environ.get("DSS_DIST_BACKEND"):
         raise SystemExit(f"[bench] multi-GPU runs must use the nccl (= RCCL) backend, got {backend}")
+    if a.dump_outputs and rank == 0:
+        Path(a.dump_outputs).mkdir(parents=True, exist_ok=True)    # an unwritable DIR fails before any GPU work
     dev = distributed.local_device()
     ranks_seen = [(rank, dev.index)]
     if world > 1:
@@ -786,8 +814,11 @@ def main():
 
     hip.TIMERS = {} if a.timer_sample > 0 else None
     hip.TIMER_SAMPLE = max(a.timer_sample, 1)
+    # the timed region reads the pool from its first chunk: how many warm-up steps --min-warmup-seconds ran must not decide
+    # which images are timed (and dumped)
     elapsed, host_enqueue_s, infos, gathered, chunk_pos = run_steps(model, feeder, counts, a, rank, world, n_patches,
-                                                                    a.w_dtype, first_chunk=chunk_pos)
+                                                                    a.w_dtype, first_chunk=0)
+    dumped = run_steps.last_outputs
     timers, hip.TIMERS = (hip.TIMERS or {}), None
     timeline = getattr(run_steps, "timeline", None)
     n_images = sum(counts)
@@ -910,6 +941,11 @@ def main():
             out["cpu_baseline"], out["parity"] = cpu_baseline(a.model, sd, a.size, a.K, a.cpu_images, first[1], first[0],
                                                               lam_tol=1e-3 if dtype == torch.float16 else 1e-2,
                                                               n_parity=a.parity_images)
+        if dumped is not None:
+            for name, arr in dumped.items():
+                np.save(Path(a.dump_outputs) / f"{name}.npy", arr)
+            print(f"[bench] --dump-outputs: eigenvalues {dumped['eigenvalues'].shape}, eigenvectors {dumped['eigenvectors'].shape} "
+                  f"of the last timed step ({counts[-1]} images) -> {a.dump_outputs}", file=sys.stderr)
         print(json.dumps(out))
     if world > 1:
         torch.distributed.barrier()

@@ -64,7 +64,9 @@ def _worker(rank, world, port, q):
         q.put(ok)
     else:
         assert got is None
-    dist.barrier()
+    # gloo's own barrier: dist.barrier() first asks the runtime for an accelerator, and on a GPU machine that query opens
+    # the GPU in every rank of this CPU-only test
+    dist.monitored_barrier()
     dist.destroy_process_group()
 
 
@@ -114,7 +116,7 @@ def _worker8(rank, world, port, total, q):
         q.put(ok)
     else:
         assert got is None
-    dist.barrier()
+    dist.monitored_barrier()         # (not dist.barrier(): see _worker)
     dist.destroy_process_group()
 
 

@@ -627,6 +627,38 @@ def test_bench_two_gpus_over_rccl():
     assert d2["config"]["images_total"] == 2 * 2 * 64 and d2["unconverged_images"] == 0
 
 
+def test_bench_steps_and_dumped_outputs_do_not_depend_on_the_warmup(tmp_path):
+    """`bench.py --steps 3 --dump-outputs DIR`: the line reports 3 timed steps and their ms_per_step, and the dumped last step
+    (eigenvalues [n, K], eigenvectors [n, K, N], float32) after one warm-up step is that after three: the timed region reads
+    the same images whatever the warm-up ran.  (Two processes agree to float32 rounding, not bit for bit: the bound is
+    the parity rule's 1 - |cos| <= 1e-4 per isolated eigenvector; other images miss it by orders of magnitude.)"""
+    import json
+    import subprocess
+    import sys
+
+    repo = Path(__file__).resolve().parents[1]
+    common = ["--gpus", "1", "--steps", "3", "--min-warmup-seconds", "0", "--cpu-images", "0", "--companion-steps", "0",
+              "--dino-like-steps", "0", "--batch", "64", "--vit-batch", "32", "--size", "224", "--distinct", "80",
+              "--gemm-tuning", "off"]
+    outs = []
+    for warmup in (1, 3):
+        d = tmp_path / f"w{warmup}"
+        r = subprocess.run([sys.executable, str(repo / "bench.py"), *common, "--warmup", str(warmup), "--dump-outputs", str(d)],
+                           capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-4000:]
+        line = json.loads(r.stdout.strip().splitlines()[-1])
+        assert line["steps"] == 3 and line["warmup_steps_run"] == warmup and line["ms_per_step"] > 0
+        assert line["config"]["images_total"] == 3 * 64 and line["unconverged_images"] == 0
+        ev, vec = np.load(d / "eigenvalues.npy"), np.load(d / "eigenvectors.npy")
+        assert ev.dtype == vec.dtype == np.float32 and ev.shape == (64, 5) and vec.shape == (64, 5, 196)
+        outs.append((ev.astype(np.float64), vec.astype(np.float64)))
+    (ev1, v1), (ev3, v3) = outs
+    assert np.abs(ev1 - ev3).max() <= 1e-5, np.abs(ev1 - ev3).max()
+    cos = np.abs((v1 * v3).sum(-1)) / (np.linalg.norm(v1, axis=-1) * np.linalg.norm(v3, axis=-1))
+    gap = np.minimum(np.diff(ev1, axis=1, prepend=-np.inf), np.diff(ev1, axis=1, append=np.inf))
+    assert (gap > 1e-3).sum() >= ev1.size // 2 and (1 - cos)[gap > 1e-3].max() <= 1e-4, (1 - cos)[gap > 1e-3].max()
+
+
 def test_cli_other_which_matrix_branches(tmp_path):
     """extract_eigs --which_matrix affinity / affinity_svd and --lapnorm False write the reference's schemas."""
     feats = synthetic.synthetic_features("blobs", 196, 384, 102, (14, 14))

@@ -180,6 +180,35 @@ def test_bench_chunking_is_balanced_and_keeps_the_copy_pipeline_fed():
                     assert all(abs(x / r - round(x / r)) < 0.02 for x in c[1:-1])   # every forward between first and last is whole rounds
 
 
+def test_bench_dump_decodes_the_host_records_and_samples_a_fixed_subset(monkeypatch):
+    """bench.last_step_outputs (--dump-outputs): the host block of one step (distributed.pack_records rows) -> eigenvalues
+    [n, K] and eigenvectors [n, K, N], float32, row for row the same image; above the byte budget a seeded sample in step
+    order, the same on every call."""
+    import importlib.util
+
+    spec = importlib.util.spec_from_file_location("bench_mod", Path(__file__).resolve().parents[1] / "bench.py")
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    rng = np.random.default_rng(3)
+    n, K, N = 37, 5, 196
+    ev = torch.from_numpy(rng.random((n, K), dtype=np.float32))
+    vec = torch.from_numpy(rng.standard_normal((n, K, N), dtype=np.float32))
+    _, flat = distributed.pack_records(torch.arange(n), ev, vec)
+    block = flat.view(n, K * N + K)
+    out = bench.last_step_outputs(block, K, N)
+    assert set(out) == {"eigenvalues", "eigenvectors"}
+    assert out["eigenvalues"].dtype == out["eigenvectors"].dtype == np.float32
+    assert np.array_equal(out["eigenvalues"], ev.numpy()) and np.array_equal(out["eigenvectors"], vec.numpy())
+    monkeypatch.setattr(bench, "DUMP_BYTES", 10 * (K * N + K) * 4 + 7)
+    s1, s2 = bench.last_step_outputs(block, K, N), bench.last_step_outputs(block, K, N)
+    assert s1["eigenvalues"].shape == (10, K) and s1["eigenvectors"].shape == (10, K, N)
+    assert sum(a_.nbytes for a_ in s1.values()) <= bench.DUMP_BYTES
+    assert all(np.array_equal(s1[k_], s2[k_]) for k_ in s1)
+    rows = [int(np.flatnonzero((ev.numpy() == r).all(1))[0]) for r in s1["eigenvalues"]]
+    assert rows == sorted(rows) and len(set(rows)) == 10
+    assert np.array_equal(s1["eigenvectors"], vec.numpy()[rows])
+
+
 def test_wave_filling_batch_picks_whole_waves_of_workgroups():
     """vit.wave_filling_batch: images per ViT forward such that ceil(b * tokens / 512) workgroups of the K-resident
     Linear kernel fill whole waves of the CUs (pure arithmetic; no GPU)."""
