@@ -27,7 +27,9 @@ The consumers of the eigen files keep the reference's names and
 from __future__ import annotations
 
 import ast
+import contextlib
 import inspect
+import math
 import os
 import threading
 import sys
@@ -166,12 +168,101 @@ def _atomic_write(writer, obj, path: str):
     os.replace(tmp, path)
 
 
-class _AsyncSaver:
-    """``torch.save`` off the critical path for SMALL runs: a thread pool (measured: serial saves of 1.4 MB feature files
-    cap the CLI at ~120 images/s; threads ~210 - pickling and the zip writer hold the GIL).  Large runs use ``_FastSaver``
-    (torch-free worker processes).  ``close()`` waits for everything and re-raises the first error."""
+def _write_png(arr, path: str):
+    from PIL import Image
 
-    procs = 0   # (no worker processes: what `_FastSaver.procs` is compared with)
+    Image.fromarray(arr).save(path, format="PNG")     # (explicit: the name may be a temporary one, see _atomic_write)
+
+
+_STALE_AFTER_S = 6 * 3600
+
+
+def _sweep_stale():
+    """Blocks of runs that were killed before their ``finally`` (names carry the owner's pid): remove those that are
+    OURS (same uid), whose process is gone AND that nobody has touched for hours - /dev/shm may be shared with other
+    PID namespaces (containers started with --ipc=host), where a live run's pid looks dead from here."""
+    import time
+
+    try:
+        names = [n for n in os.listdir("/dev/shm") if n.startswith("dss_")]
+    except OSError:
+        return
+    now, uid = time.time(), os.getuid()
+    for n in names:
+        path = os.path.join("/dev/shm", n)
+        try:
+            st = os.stat(path)
+            if st.st_uid != uid or now - max(st.st_mtime, st.st_atime) < _STALE_AFTER_S:
+                continue
+            os.kill(int(n.split("_")[1]), 0)          # raises if no such process
+        except (ProcessLookupError, ValueError, IndexError):
+            try:
+                os.unlink(path)
+            except OSError:
+                pass
+        except OSError:
+            pass                      # vanished meanwhile, or somebody else's live process
+
+
+class _ShmBlock:
+    """``nbytes`` of /dev/shm at ``path`` (``/dev/shm/dss_<pid>_...``) that worker processes map by path (``pthfast._block``)
+    and the GPU copies to or from: wrapped as the u8 ``tensor`` and page-locked (best effort; measured on the GPU box: a
+    0.69 MB H2D takes 0.024 ms out of a registered block, 0.145 ms out of an unregistered one)."""
+
+    def __init__(self, path: str, nbytes: int):
+        import mmap
+
+        self.path, self.nbytes, self.freed = path, nbytes, False
+        fd = os.open(path, os.O_CREAT | os.O_RDWR | os.O_TRUNC, 0o600)
+        try:
+            os.posix_fallocate(fd, 0, nbytes)   # the pages exist (zeroed by the kernel, no fault per page) before
+            m = mmap.mmap(fd, nbytes)            # they are page-locked
+        finally:
+            os.close(fd)
+        self.tensor = torch.frombuffer(m, dtype=torch.uint8)     # (keeps the mapping alive)
+        try:
+            torch.cuda.cudart().cudaHostRegister(self.tensor.data_ptr(), nbytes, 0)
+        except Exception:  # pragma: no cover - pageable copies still work
+            pass
+
+    def touch(self):
+        """mmap writes do not refresh a tmpfs file's times: a LIVE run's blocks must not look hours-old to another run's
+        ``_sweep_stale``."""
+        try:
+            os.utime(self.path)
+        except OSError:
+            pass
+
+    def free(self):
+        """Unregister and unlink (once; the mapping goes with the last reference to ``tensor``)."""
+        if self.freed:
+            return
+        self.freed = True
+        try:
+            torch.cuda.cudart().cudaHostUnregister(self.tensor.data_ptr())
+        except Exception:  # pragma: no cover
+            pass
+        try:
+            os.unlink(self.path)
+        except OSError:
+            pass
+
+
+class _Saver:
+    """What both savers share: ``with saver:`` closes it when the block ends and aborts it when the block raises."""
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, exc_type, *_):
+        self.close() if exc_type is None else self.abort()
+        return False
+
+
+class _AsyncSaver(_Saver):
+    """The saver of a SMALL run: ``torch.save`` on a thread pool (measured: serial saves of 1.4 MB feature files cap the CLI
+    at ~120 images/s; threads ~210 - pickling and the zip writer hold the GIL).  Large runs use ``_FastSaver`` (torch-free
+    worker processes) through the same methods.  ``close()`` waits for everything and re-raises the first error."""
 
     def __init__(self, threads: int = _IO_THREADS, max_pending: int = 1024):
         self.pool = ThreadPoolExecutor(max_workers=threads)
@@ -179,7 +270,7 @@ class _AsyncSaver:
         self.waited = 0
         self.max_pending = max_pending
 
-    def submit(self, obj, path: str, writer=torch.save):
+    def _submit(self, writer, obj, path: str):
         self.futures.append(self.pool.submit(_atomic_write, writer, obj, path))
         if len(self.futures) - self.waited >= self.max_pending:  # back-pressure: bound the queued work
             upto = self.waited + self.max_pending // 2
@@ -187,12 +278,32 @@ class _AsyncSaver:
                 f.result()
             self.waited = upto
 
-    def submit_batch(self, kind: str, tensors: Tuple[torch.Tensor, ...], items: List[tuple], chunk: int = 16,
-                     slot: Optional[int] = None):
-        """``items`` (one tuple per file, see ``_SAVE_BUILDERS[kind]``) index into the batch ``tensors`` (host tensors): the files
-        are built here and saved by the threads."""
-        for it in items:
-            self.submit(*_SAVE_BUILDERS[kind](tensors, it), writer=_SAVE_WRITERS.get(kind, torch.save))
+    def host_buffer(self, shape, dtype: torch.dtype) -> torch.Tensor:
+        """Where a batch of features is copied before ``submit_features``."""
+        return torch.empty(shape, dtype=dtype)
+
+    def submit_features(self, k: torch.Tensor, metas: List[tuple]):
+        """One feature file per ``(row of k, index, file, model_name, patch_size, shape, out path)``, the reference's schema
+        (``_feature_dict``) with that image's rows only."""
+        for j, index, file, model_name, patch_size, shape, out in metas:
+            self._submit(torch.save, _feature_dict(k[j:j + 1].clone(), index, file, model_name, patch_size, shape), out)
+
+    def submit_batch(self, kind: str, tensors: Tuple[torch.Tensor, ...], items: List[tuple]):
+        """One file per item, cut from the batch's host ``tensors``.  "eigs": tensors = (eigenvalues [B, K], eigenvectors
+        [B, K, N]), item = (row, out path, problem) -> the schema of extract/extract.py:235,243-244 (the 'affinity' branch
+        stores its eigenvalues as a raw numpy array, :171,243 - kept, consumers load it that way).  "png": tensors = (u8 label /
+        mask maps [B, N],), item = (row, out path, rows, cols) -> one 8-bit PNG."""
+        if kind == "eigs":
+            ev, vec = tensors
+            for j, out, problem in items:
+                vals = ev[j].clone()
+                self._submit(torch.save, {"eigenvalues": vals.numpy() if problem == "affinity" else vals,
+                                          "eigenvectors": vec[j].clone()}, out)
+        elif kind == "png":
+            for j, out, hp, wp in items:
+                self._submit(_write_png, tensors[0][j].reshape(hp, wp).numpy(), out)
+        else:
+            raise ValueError(kind)
 
     def close(self):
         for f in self.futures:
@@ -205,71 +316,58 @@ class _AsyncSaver:
         self.pool.shutdown(wait=False, cancel_futures=True)
 
 
-class _FastSaver:
+class _FastSaver(_Saver):
     """The savers of a LARGE run (round 5): torch-free worker processes (``pthfast.save_chunk / save_eigs / save_pngs`` - the
     archive `torch.save` would write, assembled directly) instead of processes that import torch to call it.  A saver is up
     in ~0.3 s instead of ~2 s (round 4: first feature file after 3.8 s) and costs a plain interpreter, so there can be
     dozens: a 1.4 MB feature file is ~2.7 ms of CRC + page-cache copy whoever writes it, and sixteen writers were what
     capped `extract_features` at ~5 800 images/s (`drain: shared block` = waiting for a ring slot to be written out).
-    Features travel through a ring of page-locked /dev/shm blocks the GPU copies into (``block`` / ``submit_features`` /
-    ``wait_slot``); eigenpairs and label maps are small and go through the pool's pipe (``submit_batch``)."""
+    Features travel through a ring of page-locked /dev/shm blocks the GPU copies into (``host_buffer`` /
+    ``submit_features``): a fresh segment per batch cost 90 ms of page faults plus a 1.5 GB/s pageable D2H (177 MB per 128
+    images).  Eigenpairs and label maps are small and go through the pool's pipe (``submit_batch``)."""
 
     RING = 6
 
     def __init__(self, processes: int):
         self.pool = _StaggeredPool(processes)
-        self.procs = processes                       # (truthy, like _AsyncSaver.procs: "worker processes are in use")
-        self.slots = [None] * self.RING              # (path, mmap, u8 tensor, bytes) per ring slot
+        self.ring: List[Optional[_ShmBlock]] = [None] * self.RING
         self.pending: List[List] = [[] for _ in range(self.RING + 1)]   # results per slot; [RING] = the pipe jobs
+        self.turn = self.filled = 0                  # ring slots handed out so far; the slot handed out last
+        self.done = False                            # closed or aborted: no new blocks
+        self.lock = threading.Lock()
         self.tag = f"{os.getpid()}_{id(self) & 0xffff:x}"
 
-    def block(self, slot: int, nbytes: int) -> torch.Tensor:
-        """The u8 tensor over ring block ``slot`` (grown if the batch needs more; ``wait_slot`` first)."""
-        import mmap
+    def host_buffer(self, shape, dtype: torch.dtype) -> torch.Tensor:
+        """The next ring slot's block as a ``shape`` / ``dtype`` tensor, once every file cut from its previous contents has
+        been written (grown if the batch needs more)."""
+        if self.done:
+            raise RuntimeError("the saver has been closed or aborted")
+        slot, nbytes = self.turn % self.RING, math.prod(shape) * dtype.itemsize
+        self.turn += 1
+        self._wait(slot)
+        with self.lock:                              # (an abort() from another thread frees the ring under the same lock)
+            if self.done:
+                raise RuntimeError("the saver has been closed or aborted")
+            block = self.ring[slot]
+            if block is None or block.nbytes < nbytes:
+                if block is not None:
+                    block.free()
+                block = self.ring[slot] = _ShmBlock(f"/dev/shm/dss_{self.tag}_s{slot}_{nbytes}", nbytes)
+        self.filled = slot
+        return block.tensor[:nbytes].view(dtype).view(shape)
 
-        cur = self.slots[slot]
-        if cur is None or cur[3] < nbytes:
-            self._free(slot)
-            path = f"/dev/shm/dss_{self.tag}_s{slot}_{nbytes}"
-            fd = os.open(path, os.O_CREAT | os.O_RDWR | os.O_TRUNC, 0o600)
-            try:
-                os.posix_fallocate(fd, 0, nbytes)
-                m = mmap.mmap(fd, nbytes)
-            finally:
-                os.close(fd)
-            t = torch.frombuffer(m, dtype=torch.uint8)
-            try:
-                torch.cuda.cudart().cudaHostRegister(t.data_ptr(), nbytes, 0)
-            except Exception:  # pragma: no cover - pageable copies still work
-                pass
-            self.slots[slot] = cur = (path, m, t, nbytes)
-        return cur[2]
-
-    def _free(self, slot: int):
-        cur, self.slots[slot] = self.slots[slot], None
-        if cur is None:
-            return
-        try:
-            torch.cuda.cudart().cudaHostUnregister(cur[2].data_ptr())
-        except Exception:  # pragma: no cover
-            pass
-        try:
-            os.unlink(cur[0])
-        except OSError:
-            pass
-
-    def submit_features(self, slot: int, items: List[tuple], chunk: int = 8):
-        path, _, _, nbytes = self.slots[slot]
-        try:
-            os.utime(path)                           # a live block must not look hours-old to another run's _sweep_stale
-        except OSError:
-            pass
+    def submit_features(self, k: torch.Tensor, metas: List[tuple], chunk: int = 8):
+        """``_AsyncSaver.submit_features`` for ``k`` = what ``host_buffer`` returned last: the workers cut the files from the
+        block (``pthfast.save_chunk`` takes each image's byte offset and feature shape in front of its metadata)."""
+        block, per = self.ring[self.filled], k[0].numel() * k.element_size()
+        block.touch()
+        items = [(j * per, tuple(k.shape[1:]), *meta) for j, *meta in metas]
         for s in range(0, len(items), chunk):
-            self.pending[slot].append(self.pool.apply_async(pthfast.save_chunk, (path, nbytes, "features", items[s:s + chunk])))
+            self.pending[self.filled].append(self.pool.apply_async(pthfast.save_chunk,
+                                                                   (block.path, block.nbytes, items[s:s + chunk])))
 
-    def submit_batch(self, kind: str, tensors: Tuple[torch.Tensor, ...], items: List[tuple], chunk: int = 32, slot=None):
-        """``_AsyncSaver.submit_batch`` for the small kinds: "eigs" (tensors = (eigenvalues [B, K], eigenvectors [B, K, N]), item =
-        (row, out path, problem)) and "png" (tensors = (u8 maps [B, N],), item = (row, out path, rows, cols))."""
+    def submit_batch(self, kind: str, tensors: Tuple[torch.Tensor, ...], items: List[tuple], chunk: int = 32):
+        """``_AsyncSaver.submit_batch`` (the "eigs" problem is never 'affinity' here, see ``_open_saver``)."""
         if kind == "eigs":
             ev, vec = (t.numpy() for t in tensors)
             jobs, fn = [(ev[j], vec[j], out) for j, out, _ in items], pthfast.save_eigs
@@ -284,132 +382,47 @@ class _FastSaver:
         for s in range(0, len(jobs), chunk):
             done.append(self.pool.apply_async(fn, (jobs[s:s + chunk],)))
 
-    def wait_slot(self, slot: int):
+    def _wait(self, slot: int):
         for r in self.pending[slot]:
             r.get(timeout=600)                       # re-raises what the worker raised
         self.pending[slot].clear()
 
     def close(self):
+        if self.done:
+            return
         try:
             for slot in range(self.RING + 1):
-                self.wait_slot(slot)
+                self._wait(slot)
             self.pool.__exit__(None, None, None)
         except BaseException:
             self.pool.__exit__(RuntimeError, None, None)
             raise
         finally:
-            for slot in range(self.RING):
-                self._free(slot)
+            self._free_ring()
 
     def abort(self):
         """The run failed (worker / GPU / decode error, Ctrl-C): stop the workers and give the page-locked /dev/shm blocks back
         NOW - `_sweep_stale` would only collect them hours later (up to RING blocks of ~0.8 GB each)."""
+        if self.done:
+            return
+        self.done = True
         try:
             self.pool.__exit__(RuntimeError, None, None)
         finally:
-            for slot in range(self.RING):
-                self._free(slot)
+            self._free_ring()
+
+    def _free_ring(self):
+        with self.lock:
+            self.done = True
+            for block in self.ring:
+                if block is not None:
+                    block.free()
 
 
-def _build_feature_file(tensors, item):
-    (k,), (j, idx, file, model_name, patch_size, shape, out) = tensors, item
-    return _feature_dict(k[j:j + 1].clone(), idx, file, model_name, patch_size, shape), out
-
-
-def _build_eig_file(tensors, item):
-    # schema of extract/extract.py:235,243-244: eigenvalues [K] f32, eigenvectors [K, N] f32; the 'affinity' branch
-    # stores its eigenvalues as a raw numpy array (:171,243) - kept, consumers load it that way
-    (ev, vec), (j, out, problem) = tensors, item
-    vals = ev[j].clone()
-    return {"eigenvalues": vals.numpy() if problem == "affinity" else vals, "eigenvectors": vec[j].clone()}, out
-
-
-def _build_png_file(tensors, item):
-    (labels,), (j, out, hp, wp) = tensors, item       # u8 [B, N] label / mask maps -> one 8-bit PNG per image
-    return labels[j].reshape(hp, wp).numpy(), out
-
-
-def _write_png(arr, path: str):
-    from PIL import Image
-
-    Image.fromarray(arr).save(path, format="PNG")     # (explicit: the name may be a temporary one, see _atomic_write)
-
-
-_SAVE_BUILDERS = {"features": _build_feature_file, "eigs": _build_eig_file, "png": _build_png_file}
-_SAVE_WRITERS = {"png": _write_png}     # everything else: torch.save
-
-
-class _ShmBlocks:
-    """Up to ``count`` blocks of ``size`` bytes in /dev/shm that worker processes fill (``pthfast`` maps them by path)
-    and the GPU reads: every block is wrapped as a u8 tensor and page-locked (best effort; measured on the GPU box: a
-    0.69 MB H2D takes 0.024 ms out of a registered block, 0.145 ms out of an unregistered one).  Blocks are created one
-    at a time (``add``) so that the first workers are busy while the later blocks are still being set up."""
-
-    def __init__(self, count: int, size: int):
-        self.count, self.size, self.paths, self.maps, self.tensors = count, size, [], [], []
-        self._sweep_stale()
-
-    STALE_AFTER_S = 6 * 3600
-
-    @staticmethod
-    def _sweep_stale():
-        """Blocks of runs that were killed before their ``finally`` (names carry the owner's pid): remove those that are
-        OURS (same uid), whose process is gone AND that nobody has touched for hours - /dev/shm may be shared with other
-        PID namespaces (containers started with --ipc=host), where a live run's pid looks dead from here."""
-        import time
-
-        try:
-            names = [n for n in os.listdir("/dev/shm") if n.startswith("dss_")]
-        except OSError:
-            return
-        now, uid = time.time(), os.getuid()
-        for n in names:
-            path = os.path.join("/dev/shm", n)
-            try:
-                st = os.stat(path)
-                if st.st_uid != uid or now - max(st.st_mtime, st.st_atime) < _ShmBlocks.STALE_AFTER_S:
-                    continue
-                os.kill(int(n.split("_")[1]), 0)          # raises if no such process
-            except (ProcessLookupError, ValueError, IndexError):
-                try:
-                    os.unlink(path)
-                except OSError:
-                    pass
-            except OSError:
-                pass                      # vanished meanwhile, or somebody else's live process
-
-    def add(self) -> int:
-        import mmap
-
-        i = len(self.paths)
-        path = f"/dev/shm/dss_{os.getpid()}_{id(self) & 0xffff:x}_{i}"
-        fd = os.open(path, os.O_CREAT | os.O_RDWR | os.O_TRUNC, 0o600)
-        try:
-            os.posix_fallocate(fd, 0, self.size)   # the pages exist (zeroed by the kernel, no fault per page) before
-            m = mmap.mmap(fd, self.size)           # they are page-locked
-        finally:
-            os.close(fd)
-        t = torch.frombuffer(m, dtype=torch.uint8)
-        try:
-            torch.cuda.cudart().cudaHostRegister(t.data_ptr(), self.size, 0)
-        except Exception:  # pragma: no cover - pageable copies still work
-            pass
-        self.paths.append(path), self.maps.append(m), self.tensors.append(t)
-        return i
-
-    def close(self):
-        for t in self.tensors:
-            try:
-                torch.cuda.cudart().cudaHostUnregister(t.data_ptr())
-            except Exception:  # pragma: no cover
-                pass
-        self.tensors.clear()
-        for path in self.paths:
-            try:
-                os.unlink(path)
-            except OSError:
-                pass
-        self.paths.clear()
+def _open_saver(processes: int, affinity: bool = False) -> "_AsyncSaver | _FastSaver":
+    """The process saver for ``processes > 0``, the thread saver otherwise - and always for the 'affinity' branch: it stores
+    its eigenvalues as a raw numpy array (extract/extract.py:171,243), which only ``torch.save`` writes."""
+    return _FastSaver(processes) if processes > 0 and not affinity else _AsyncSaver()
 
 
 def _pump_chunks(fn, chunks: List[list], extra_args: tuple, processes: int, block_bytes: int):
@@ -422,11 +435,14 @@ def _pump_chunks(fn, chunks: List[list], extra_args: tuple, processes: int, bloc
     import time
     t_start = time.perf_counter()
     pool = _StaggeredPool(processes)                 # the first wave boots while the blocks are pinned
-    blocks = _ShmBlocks(processes + 2, block_bytes)
+    _sweep_stale()
+    # up to processes + 2 blocks, created one at a time: the first workers are busy while the later blocks are set up
+    blocks: List[_ShmBlock] = []
+    tag = f"{os.getpid()}_{id(blocks) & 0xffff:x}"
     first = None
     try:
         with pool:
-            free, events = deque(), [None] * blocks.count
+            free, events = deque(), [None] * (processes + 2)
             pending, nxt = deque(), 0
 
             def releaser(b):
@@ -437,26 +453,54 @@ def _pump_chunks(fn, chunks: List[list], extra_args: tuple, processes: int, bloc
                 return release
 
             while nxt < len(chunks) or pending:
-                while (free or len(blocks.paths) < blocks.count) and nxt < len(chunks) and len(pending) < pool.capacity() + 2:
-                    b = free.popleft() if free else blocks.add()
-                    if events[b] is not None:
+                while (free or len(blocks) < len(events)) and nxt < len(chunks) and len(pending) < pool.capacity() + 2:
+                    if free:
+                        b = free.popleft()
                         events[b].synchronize()     # the copies out of this block have finished
-                        try:                        # (mmap writes do not refresh a tmpfs file's times: a LIVE run's blocks must
-                            os.utime(blocks.paths[b])   # not look hours-old to another run's _sweep_stale)
-                        except OSError:
-                            pass
-                    pending.append((pool.apply_async(fn, (blocks.paths[b], blocks.size, chunks[nxt]) + extra_args), b))
+                        blocks[b].touch()
+                    else:
+                        b = len(blocks)
+                        blocks.append(_ShmBlock(f"/dev/shm/dss_{tag}_{b}", block_bytes))
+                    pending.append((pool.apply_async(fn, (blocks[b].path, block_bytes, chunks[nxt]) + extra_args), b))
                     nxt += 1
                 res, b = pending.popleft()
                 got = res.get(timeout=600)          # a lost worker must not hang the run
                 if first is None:
                     first = time.perf_counter() - t_start
-                yield got, blocks.tensors[b], releaser(b)
+                yield got, blocks[b].tensor, releaser(b)
     finally:
-        blocks.close()
+        for block in blocks:
+            block.free()
         if os.environ.get("DSS_CLI_TIMING") and first is not None:
             print(f"[dss] {fn.__name__}: {processes} workers ({_start_method()}, waves of {pool.WAVE}), first chunk after {first:.2f} s, "
                   f"all {len(chunks)} chunks after {time.perf_counter() - t_start:.2f} s")
+
+
+def _pump_to_device(fn, paths: List[str], extra_args: tuple, processes: int, bytes_per_path: int, dtype: torch.dtype,
+                    device: torch.device):
+    """``_pump_chunks`` over chunks of 16 of ``paths``, where ``fn`` returns ``(byte offset, shape, meta)`` per path.  Yields
+    per path, in order, ``(meta, device tensor)`` - or ``(reason, None)`` for a path the worker left to the parent (offset
+    None).  ONE non-blocking H2D copy per run of same-shape entries that lie back to back in the block (a whole chunk on a
+    one-size dataset) instead of one per entry: 20 480 copy calls were ~1 s of the main thread's 8 s at 5 000 images/s."""
+    per, size = 16, dtype.itemsize
+    chunks = [paths[s:s + per] for s in range(0, len(paths), per)]
+    with contextlib.closing(_pump_chunks(fn, chunks, extra_args, processes, per * bytes_per_path)) as pumped:
+        for entries, block, release in pumped:
+            i = 0
+            while i < len(entries):
+                off, shape, meta = entries[i]
+                if off is None:
+                    yield meta, None
+                    i += 1
+                    continue
+                n, j = math.prod(shape) * size, i + 1
+                while j < len(entries) and entries[j][1] == shape and entries[j][0] == off + (j - i) * n:
+                    j += 1
+                dev = block[off:off + (j - i) * n].view(dtype).view((j - i,) + tuple(shape)).to(device, non_blocking=True)
+                for q in range(j - i):
+                    yield entries[i + q][2], dev[q]
+                i = j
+            release()
 
 
 class _StaggeredPool:
@@ -549,34 +593,19 @@ def _iter_features(files, which_features: str, processes: int, window: int, devi
     """Yields ``(data_dict without the features, features [N, D] f32)`` for every file of ``files``, in order.  Small
     runs: ``torch.load`` on a thread pool, host tensors.  Large runs on a GPU: ``processes`` torch-free loader processes
     (``pthfast.load_chunk``) read chunks of 16 files straight into page-locked /dev/shm blocks; the rows are copied to
-    ``device`` from there (one async H2D per run of same-shape files) and yielded as DEVICE tensors."""
+    ``device`` from there (``_pump_to_device``) and yielded as DEVICE tensors."""
     if processes <= 0 or device is None or device.type != "cuda":
         with ThreadPoolExecutor(max_workers=_IO_THREADS) as pool:
             yield from _bounded_map(pool, lambda f: _load_features(str(f), which_features), files, window)
         return
-    per = 16
-    chunks = [[str(f) for f in files[s:s + per]] for s in range(0, len(files), per)]
+    paths = [str(f) for f in files]
     # a file's size bounds its feature bytes AS STORED; the loaders hand them over as f32: f16 / bf16 features (half the
     # file) need twice the file's size in the block - sized for that, or half of such files would fall back to torch.load
-    biggest = 2 * max(os.path.getsize(f) for f in files)
-    for entries, block, release in _pump_chunks(pthfast.load_chunk, chunks, (which_features,), processes, per * biggest):
-        i = 0
-        while i < len(entries):
-            meta, off, shape = entries[i]
-            if meta is None:                # (None, file, reason): not a plain feature archive
-                yield _load_features(off, which_features)
-                i += 1
-                continue
-            j, nbytes = i + 1, 4 * shape[0] * shape[1]
-            while j < len(entries) and entries[j][0] is not None and entries[j][2] == shape \
-                    and entries[j][1] == off + (j - i) * nbytes:
-                j += 1
-            rows = block[off:off + (j - i) * nbytes].view(torch.float32).view((j - i,) + tuple(shape))
-            dev = rows.to(device, non_blocking=True)
-            for n in range(j - i):
-                yield entries[i + n][0], dev[n]
-            i = j
-        release()
+    biggest = 2 * max(os.path.getsize(f) for f in paths)
+    with contextlib.closing(_pump_to_device(pthfast.load_chunk, paths, (which_features,), processes, biggest, torch.float32,
+                                            device)) as loaded:
+        for (meta, feats), path in zip(loaded, paths):
+            yield (meta, feats) if feats is not None else _load_features(path, which_features)   # not a plain feature archive
 
 
 def _iter_images(dataset, todo, processes: int, window: int, device: torch.device):
@@ -591,31 +620,12 @@ def _iter_images(dataset, todo, processes: int, window: int, device: torch.devic
         with ThreadPoolExecutor(max_workers=_IO_THREADS) as pool:  # decode pool (the reference: 8 loader processes)
             yield from _bounded_map(pool, decode, todo, window)
         return
-    per = 16
     names = [dataset.filenames[i] for i, _ in todo]
     paths = [str(n if dataset.root is None else dataset.root / n) for n in names]
-    chunks = [paths[s:s + per] for s in range(0, len(paths), per)]
-    at = 0
     # 1.5 MB per image on average (VOC: <= 500 x 500 x 3 = 0.75 MB); what does not fit a block is decoded here
-    for entries, block, release in _pump_chunks(pthfast.decode_chunk, chunks, (), processes, per * (3 << 19)):
-        i = 0
-        while i < len(entries):
-            off, shape = entries[i]
-            if off is None:                # did not fit the block: decode it here
-                yield dataset[todo[at][0]][0].to(device), names[at]
-                at, i = at + 1, i + 1
-                continue
-            # ONE H2D copy per run of same-shape images that lie back to back in the block (a whole chunk on a one-size
-            # dataset) instead of one per image: 20 480 copy calls were ~1 s of the main thread's 8 s at 5 000 images/s
-            n, j = shape[0] * shape[1] * shape[2], i + 1
-            while j < len(entries) and entries[j][1] == shape and entries[j][0] == off + (j - i) * n:
-                j += 1
-            dev = block[off:off + (j - i) * n].view((j - i,) + tuple(shape)).to(device, non_blocking=True)
-            for q in range(j - i):
-                yield dev[q], names[at]
-                at += 1
-            i = j
-        release()
+    with contextlib.closing(_pump_to_device(pthfast.decode_chunk, paths, (), processes, 3 << 19, torch.uint8, device)) as decoded:
+        for (_, img), (i, _), name in zip(decoded, todo, names):
+            yield (img if img is not None else dataset[i][0].to(device)), name
 
 
 def _shm_free_bytes() -> int:
@@ -706,110 +716,110 @@ def extract_features(images_list: str, images_root: Optional[str], model_name: s
 
     bs = int(batch_size)
     clock = _StageClock()
-    with clock("start savers"):   # first of all: the saver processes boot while the model is being built
-        n_savers = _io_processes(len(todo), most=32, env="DSS_SAVER_PROCESSES")
-        saver = _FastSaver(n_savers) if n_savers > 0 else _AsyncSaver()
-    # ~6.5 ms of PIL per 480 x 480 JPEG (150 images/s per process): the ViT takes 12 000 images/s, the feature savers
-    # ~1 000 files/s each - dozens of decoders (started in waves of twelve, _StaggeredPool) before the GPU is what waits
-    decoders = _io_processes(len(todo), most=48) if saver.procs else 0
-    try:
+    # Everything the run opens lives in `stack`; on the way out - an error included - the decoded-image generator is closed
+    # first (its decoder processes stopped, their /dev/shm blocks unlinked), then the drain thread is stopped, then the
+    # saver is closed (aborted on an error: workers stopped, its /dev/shm ring unlinked at once).
+    with contextlib.ExitStack() as stack:
+        with clock("start savers"):   # first of all: the saver processes boot while the model is being built
+            n_savers = _io_processes(len(todo), most=32, env="DSS_SAVER_PROCESSES")
+            saver = stack.enter_context(_open_saver(n_savers))
+        # ~6.5 ms of PIL per 480 x 480 JPEG (150 images/s per process): the ViT takes 12 000 images/s, the feature savers
+        # ~1 000 files/s each - dozens of decoders (started in waves of twelve, _StaggeredPool) before the GPU is what waits
+        decoders = _io_processes(len(todo), most=48) if n_savers > 0 else 0
         with clock("model"):
             model, _, patch_size, _ = utils.get_model(model_name, device=device, dtype=_DTYPES[str(dtype).lower()],
                                                       weights=weights, synthetic_seed=synthetic_weights, gelu=gelu)
-    except BaseException:
-        saver.abort()      # (the saver processes were started first: a bad checkpoint path must not leave them behind)
-        raise
 
-    # One batch travels: page-locked decoded images -> async H2D + ViT -> a drain thread that waits for the batch, copies
-    # the features into a page-locked shared-memory block the saver processes map and hands the files over.  The main
-    # thread is back at the decoded-image queue while the GPU and the drain thread work on the previous batches.
-    import queue as _queue
-    import threading
-    ring = {"next": 0}
-    copy_stream = torch.cuda.Stream(device=device)
-    drain_q: "_queue.Queue" = _queue.Queue(maxsize=3)
-    drain_err: List[BaseException] = []
+        # One batch travels: page-locked decoded images -> async H2D + ViT -> a drain thread that waits for the batch, copies
+        # the features into the saver's host buffer (for the saver processes: a page-locked shared-memory block they map)
+        # and hands the files over.  The main thread is back at the decoded-image queue while the GPU and the drain thread
+        # work on the previous batches.
+        import queue
+        copy_stream = torch.cuda.Stream(device=device)
+        drain_q: "queue.Queue" = queue.Queue(maxsize=3)
+        drain_err: List[BaseException] = []
+        stopping = threading.Event()
 
-    def drain():
-        torch.cuda.set_device(device)      # the current device is per THREAD: without this a rank with LOCAL_RANK != 0 would
-        while True:                        # register its blocks (and create a context) on GPU 0 from here
-            job = drain_q.get()
-            if job is None:
+        def drain():
+            torch.cuda.set_device(device)      # the current device is per THREAD: without this a rank with LOCAL_RANK != 0 would
+            while not stopping.is_set():       # register its blocks (and create a context) on GPU 0 from here
+                job = drain_q.get()
+                if job is None:
+                    return
+                try:
+                    k_dev, done, metas = job
+                    job = None                 # the queue item must not keep the batch's HBM alive past `del k_dev`
+                    with clock("drain: shared block"):
+                        k = saver.host_buffer(k_dev.shape, k_dev.dtype)
+                    with clock("drain: wait + D2H"), torch.cuda.stream(copy_stream):   # not behind the next batch's ViT
+                        copy_stream.wait_event(done)
+                        k_dev.record_stream(copy_stream)
+                        k.copy_(k_dev, non_blocking=True)
+                        copy_stream.synchronize()
+                    del k_dev
+                    with clock("drain: hand to savers"):
+                        saver.submit_features(k, metas)
+                except BaseException as e:  # re-raised by the main thread
+                    drain_err.append(e)
+
+        drainer = threading.Thread(target=drain, daemon=True)
+        drainer.start()
+
+        def stop_drain(exc_type=None, *_):
+            """After the last batch: the thread works through the queue.  On an error it stops after the batch in hand: the
+            flag, and the queue emptied so that the sentinel cannot be refused - then it is waited for, at most a minute."""
+            if exc_type is not None:
+                stopping.set()
+                try:
+                    while True:
+                        drain_q.get_nowait()
+                except queue.Empty:
+                    pass
+            drain_q.put(None)
+            drainer.join(timeout=None if exc_type is None else 60)
+
+        stack.push(stop_drain)
+
+        def flush(batch: List[Tuple[int, Path, torch.Tensor, str]]):
+            if not batch:
                 return
-            try:
-                k_dev, done, metas = job
-                job = None                 # the queue item must not keep the batch's HBM alive past `del k_dev`
-                slot = None
-                with clock("drain: shared block"):
-                    if saver.procs:
-                        # a ring of page-locked /dev/shm blocks the saver processes map by path: a fresh segment per batch
-                        # cost 90 ms of page faults plus a 1.5 GB/s pageable D2H (177 MB per 128 images)
-                        slot = ring["next"] % saver.RING
-                        ring["next"] += 1
-                        saver.wait_slot(slot)          # every file cut from the block's previous contents has been written
-                        nbytes = k_dev.numel() * k_dev.element_size()
-                        k = saver.block(slot, nbytes)[:nbytes].view(k_dev.dtype).view(k_dev.shape)
-                    else:
-                        k = torch.empty(k_dev.shape, dtype=k_dev.dtype)
-                with clock("drain: wait + D2H"), torch.cuda.stream(copy_stream):   # not behind the next batch's ViT
-                    copy_stream.wait_event(done)
-                    k_dev.record_stream(copy_stream)
-                    k.copy_(k_dev, non_blocking=True)
-                    copy_stream.synchronize()
-                del k_dev
-                with clock("drain: hand to savers"):
-                    if saver.procs:
-                        per = k[0].numel() * k.element_size()
-                        saver.submit_features(slot, [(j * per, tuple(k.shape[1:]), idx, file, mname, psize, shp, out)
-                                                     for j, idx, file, mname, psize, shp, out in metas])
-                    else:
-                        saver.submit_batch("features", (k,), metas)
-            except BaseException as e:  # re-raised by the main thread
-                drain_err.append(e)
+            if drain_err:
+                raise drain_err[0]
+            with clock("flush: enqueue H2D + ViT"):
+                # no host-side stacking pass: torch.stack of 128 decoded images into fresh pageable memory cost 265 ms
+                # the images arrive page-locked (decode threads) or already on the device (decoder processes): one call
+                # gathers the batch - every Python-level call gives the GIL away and queues to get it back
+                imgs = torch.empty((len(batch),) + tuple(batch[0][2].shape), dtype=torch.uint8, device=device)
+                torch._foreach_copy_(list(imgs.unbind(0)), [b[2] for b in batch], non_blocking=True)
+                k_dev = model.extract_k(imgs, which_block=which_block)
+                done = torch.cuda.Event()
+                done.record()
+            shp = (1, 3, int(imgs.shape[1]), int(imgs.shape[2]))
+            with clock("flush: drain queue full"):
+                drain_q.put((k_dev, done, [(j, idx, file, model_name, patch_size, shp, str(out))
+                                           for j, (idx, out, _, file) in enumerate(batch)]))
+            batch.clear()
 
-    drainer = threading.Thread(target=drain, daemon=True)
-    drainer.start()
+        # Real datasets (VOC) mix image sizes: bucket by shape so every ViT launch is a full same-shape batch.  At most
+        # `max_pending` decoded images wait in the buckets; beyond that the fullest bucket is flushed early.
+        # The batch size is PER SHAPE BUCKET (a dataset's first image says nothing about the others): `batch_size <= 0` gives each
+        # shape four rounds of the K-resident Linear kernels' workgroups, and every bucket is clamped to the kernels' 32-bit row
+        # limits (`bucket_batch`: M * 4 D and M * T below 2^32, the formula bench.py applies).  What waits in the buckets is bounded
+        # in BYTES of decoded images (`max_pending_bytes`), not in images.
+        buckets: Dict[Tuple[int, ...], List[Tuple[int, Path, torch.Tensor, str]]] = {}
+        auto_bs = bs <= 0
+        cus = torch.cuda.get_device_properties(device).multi_processor_count
+        rows_wg = spectral.hip.LINEAR_KRES_WIDTHS.get(model.embed_dim, (None, 256))[1]
+        bs_of: Dict[Tuple[int, ...], int] = {}
 
-    def flush(batch: List[Tuple[int, Path, torch.Tensor, str]]):
-        if not batch:
-            return
-        if drain_err:
-            raise drain_err[0]
-        with clock("flush: enqueue H2D + ViT"):
-            # no host-side stacking pass: torch.stack of 128 decoded images into fresh pageable memory cost 265 ms
-            # the images arrive page-locked (decode threads) or already on the device (decoder processes): one call
-            # gathers the batch - every Python-level call gives the GIL away and queues to get it back
-            imgs = torch.empty((len(batch),) + tuple(batch[0][2].shape), dtype=torch.uint8, device=device)
-            torch._foreach_copy_(list(imgs.unbind(0)), [b[2] for b in batch], non_blocking=True)
-            k_dev = model.extract_k(imgs, which_block=which_block)
-            done = torch.cuda.Event()
-            done.record()
-        shp = (1, 3, int(imgs.shape[1]), int(imgs.shape[2]))
-        with clock("flush: drain queue full"):
-            drain_q.put((k_dev, done, [(j, idx, file, model_name, patch_size, shp, str(out))
-                                       for j, (idx, out, _, file) in enumerate(batch)]))
-        batch.clear()
+        def bucket_bs(shape) -> int:
+            if shape not in bs_of:
+                bs_of[shape] = bucket_batch(shape[0], shape[1], patch_size, model.embed_dim, bs if not auto_bs else 0, cus, rows_wg)
+            return bs_of[shape]
 
-    # Real datasets (VOC) mix image sizes: bucket by shape so every ViT launch is a full same-shape batch.  At most
-    # `max_pending` decoded images wait in the buckets; beyond that the fullest bucket is flushed early.
-    # The batch size is PER SHAPE BUCKET (a dataset's first image says nothing about the others): `batch_size <= 0` gives each
-    # shape four rounds of the K-resident Linear kernels' workgroups, and every bucket is clamped to the kernels' 32-bit row
-    # limits (`bucket_batch`: M * 4 D and M * T below 2^32, the formula bench.py applies).  What waits in the buckets is bounded
-    # in BYTES of decoded images (`max_pending_bytes`), not in images.
-    buckets: Dict[Tuple[int, ...], List[Tuple[int, Path, torch.Tensor, str]]] = {}
-    auto_bs = bs <= 0
-    cus = torch.cuda.get_device_properties(device).multi_processor_count
-    rows_wg = spectral.hip.LINEAR_KRES_WIDTHS.get(model.embed_dim, (None, 256))[1]
-    bs_of: Dict[Tuple[int, ...], int] = {}
-
-    def bucket_bs(shape) -> int:
-        if shape not in bs_of:
-            bs_of[shape] = bucket_batch(shape[0], shape[1], patch_size, model.embed_dim, bs if not auto_bs else 0, cus, rows_wg)
-        return bs_of[shape]
-
-    max_pending_bytes, pending_bytes = 6 << 30, 0
-    decoded = _iter_images(dataset, todo, decoders, 4 * (max(1, bs) if not auto_bs else 512), device)
-    try:
+        max_pending_bytes, pending_bytes = 6 << 30, 0
+        decoded = stack.enter_context(contextlib.closing(
+            _iter_images(dataset, todo, decoders, 4 * (max(1, bs) if not auto_bs else 512), device)))
         for idx, out in todo:
             with clock("wait for decoded image"):
                 img, file = next(decoded)
@@ -826,22 +836,13 @@ def extract_features(images_list: str, images_root: Optional[str], model_name: s
                 flush(fullest)
         for bucket in buckets.values():
             flush(bucket)
+        # the clean end, timed (the stack's own calls of these two find nothing left to do)
         with clock("tail: drain thread"):
-            drain_q.put(None)
-            drainer.join()
+            stop_drain()
         if drain_err:
             raise drain_err[0]
         with clock("tail: savers finish"):
             saver.close()
-    except BaseException:
-        # decode / GPU / worker error or Ctrl-C: the drain thread is told to stop, the workers are stopped and the page-locked
-        # /dev/shm ring is unlinked before the error leaves (the blocks used to stay until the 6 h stale sweep)
-        try:
-            drain_q.put_nowait(None)
-        except Exception:
-            pass
-        saver.abort()
-        raise
     clock.report("extract_features")
     _barrier()
     print(f"Saved features to {output_dir}")
@@ -918,7 +919,7 @@ def _lr_grid(data_dict: dict, image_downsample_factor: Optional[int]) -> Tuple[i
 
 
 def _run_eig_batch(items: List[Tuple[str, torch.Tensor]], K: int, normalize: bool, threshold_at_zero: bool,
-                   device: torch.device, saver: Optional["_AsyncSaver"] = None, problem: str = "laplacian",
+                   device: torch.device, saver: "_AsyncSaver | _FastSaver", problem: str = "laplacian",
                    upsample=None, color=None, color_items: Optional[List[Tuple[str, Tuple[int, int]]]] = None,
                    segment: Optional[dict] = None):
     # straight from wherever the loader left each file's features (a shared-memory segment when worker processes read
@@ -949,12 +950,7 @@ def _run_eig_batch(items: List[Tuple[str, torch.Tensor]], K: int, normalize: boo
     if bad:
         print(f"[dss] WARNING: eigensolver did not converge for {[items[j][0] for j in bad]} (saved as is)")
     # the eigen files first: whatever happens in the optional segmentation below, the batch's results are on their way
-    ev_h, vec_h = ev.cpu(), vec.cpu()
-    if saver is None:
-        for j, (output_file, _) in enumerate(items):
-            torch.save(*_build_eig_file((ev_h, vec_h), (j, output_file, problem)))
-    else:
-        saver.submit_batch("eigs", (ev_h, vec_h), [(j, output_file, problem) for j, (output_file, _) in enumerate(items)])
+    saver.submit_batch("eigs", (ev.cpu(), vec.cpu()), [(j, output_file, problem) for j, (output_file, _) in enumerate(items)])
     if segment is not None:
         # the segmentations of extract.py:283-426 straight from the device-resident eigenvectors,
         # no .pth round trip (same algorithms on the device: threshold of the Fiedler vector; Lloyd K-means + border vote)
@@ -975,13 +971,8 @@ def _run_eig_batch(items: List[Tuple[str, torch.Tensor]], K: int, normalize: boo
             pngs.append((segment["multi_region_dir"], torch.cat(maps)))
         for out_dir, maps in pngs:
             maps = maps.cpu()
-            png_items = [(j, str(Path(out_dir) / f"{Path(output_file).stem}.png"), hp, wp)
-                         for j, (output_file, _) in enumerate(items)]
-            if saver is None:
-                for it in png_items:
-                    _write_png(*_build_png_file((maps,), it))
-            else:
-                saver.submit_batch("png", (maps,), png_items)
+            saver.submit_batch("png", (maps,), [(j, str(Path(out_dir) / f"{Path(output_file).stem}.png"), hp, wp)
+                                                for j, (output_file, _) in enumerate(items)])
 
 
 def _extract_eig(inp: Tuple[int, str], K: int, images_root: str, output_dir: str,
@@ -1001,9 +992,10 @@ def _extract_eig(inp: Tuple[int, str], K: int, images_root: str, output_dir: str
                                  data_dict["patch_size"])
     utils.get_image_sizes(data_dict)  # keeps the reference's B == 1 assertion
     color = _color_spec(which_matrix, which_color_matrix, image_color_lambda, images_root)
-    _run_eig_batch([(output_file, feats)], K, normalize, threshold_at_zero, local_device(), problem=problem,
-                   upsample=_upsample_spec(data_dict, which_matrix, image_downsample_factor), color=color,
-                   color_items=[(image_id, _lr_grid(data_dict, image_downsample_factor))])
+    with _AsyncSaver() as saver:
+        _run_eig_batch([(output_file, feats)], K, normalize, threshold_at_zero, local_device(), saver, problem=problem,
+                       upsample=_upsample_spec(data_dict, which_matrix, image_downsample_factor), color=color,
+                       color_items=[(image_id, _lr_grid(data_dict, image_downsample_factor))])
 
 
 def extract_eigs(images_root: str, features_dir: str, output_dir: str, which_matrix: str = "laplacian",
@@ -1062,12 +1054,13 @@ def extract_eigs(images_root: str, features_dir: str, output_dir: str, which_mat
     # torch.load of a 1.4 MB feature file costs ~0.6 ms and torch.save of an 18 KB eigen file less: few workers do
     nproc = _io_processes(len(mine), most=16)
     clock = _StageClock()
-    with clock("start savers"):
-        # (the 'affinity' branch stores its eigenvalues as a raw numpy array - extract.py:171,243 -: `torch.save` on threads)
-        saver = _FastSaver(min(nproc, 8)) if nproc > 0 and which_matrix != "affinity" else _AsyncSaver()
-    loaded = _iter_features(mine, which_features, nproc, 4 * bs, device)
-    scheduled = set()
-    try:
+    # on the way out, an error included: the feature generator is closed first (its loader processes stopped, their
+    # /dev/shm blocks unlinked), then the saver is closed - aborted on an error
+    with contextlib.ExitStack() as stack:
+        with clock("start savers"):
+            saver = stack.enter_context(_open_saver(min(nproc, 8), affinity=which_matrix == "affinity"))
+        loaded = stack.enter_context(contextlib.closing(_iter_features(mine, which_features, nproc, 4 * bs, device)))
+        scheduled = set()
         while True:
             with clock("wait for loaded features"):
                 nxt = next(loaded, None)
@@ -1106,9 +1099,6 @@ def extract_eigs(images_root: str, features_dir: str, output_dir: str, which_mat
                 run(key)
         with clock("tail: savers finish"):
             saver.close()
-    except BaseException:
-        saver.abort()        # stop the workers, unlink the /dev/shm ring before the error leaves
-        raise
     clock.report("extract_eigs")
     _barrier()
 

@@ -187,8 +187,8 @@ def _block(path: str, size: int) -> mmap.mmap:
 
 def load_chunk(block_path: str, block_size: int, files: List[str], which_features: str):
     """Worker entry.  Reads ``data_dict[which_features]`` of every file of ``files`` as float32 rows, packed one after
-    the other from byte 0 of the shared block.  Returns one entry per file, in order:
-    ``(meta, byte offset, (N, D))`` or ``(None, file, reason)`` for a file the parent has to load itself.
+    the other from byte 0 of the shared block.  Returns one entry per file, in order (the entry shape of ``decode_chunk``):
+    ``(byte offset, (N, D), meta)``, or ``(None, None, reason)`` for a file the parent has to load itself.
     ``meta``: the pickled dict without tensors, tensors of <= 16 elements as Python values."""
     buf = memoryview(_block(block_path, block_size))
     out, used = [], 0
@@ -218,12 +218,12 @@ def load_chunk(block_path: str, block_size: int, files: List[str], which_feature
                             meta[k] = pth.read(v).tolist()
                     else:
                         meta[k] = v
-            out.append((meta, used, shape))
+            out.append((used, shape, meta))
             used += nbytes
         except ValueError:
             raise
         except Exception as e:   # the parent falls back to torch.load for this file
-            out.append((None, str(f), f"{type(e).__name__}: {e}"))
+            out.append((None, None, f"{type(e).__name__}: {e}"))
     return out
 
 
@@ -238,18 +238,18 @@ def decode_rgb(path) -> np.ndarray:
 
 def decode_chunk(block_path: str, block_size: int, files: List[str]):
     """Worker entry of ``extract_features``: decodes ``files`` into the shared block, packed from byte 0.  One entry per
-    file, in order: ``(byte offset, (H, W, 3))``, or ``(None, reason)`` when the image does not fit what is left of the
-    block (the parent decodes it itself).  Decoding in PROCESSES: thirty decode threads keep the parent's GIL ~80 % busy
+    file, in order (the entry shape of ``load_chunk``): ``(byte offset, (H, W, 3), None)``, or ``(None, None, reason)`` when
+    the image does not fit what is left of the block (the parent decodes it itself).  Decoding in PROCESSES: thirty decode threads keep the parent's GIL ~80 % busy
     with their Python-level steps, and every kernel launch of the ViT then queues for it (100 ms per 128-image batch)."""
     buf = np.frombuffer(_block(block_path, block_size), dtype=np.uint8)
     out, used = [], 0
     for f in files:
         img = decode_rgb(f)
         if used + img.size > block_size:
-            out.append((None, "block full"))
+            out.append((None, None, "block full"))
             continue
         buf[used:used + img.size] = img.reshape(-1)
-        out.append((used, tuple(img.shape)))
+        out.append((used, tuple(img.shape), None))
         used += img.size
     return out
 
@@ -353,27 +353,17 @@ def write_pth(path: str, obj) -> None:
     os.replace(tmp, path)
 
 
-def save_chunk(block_path: str, block_size: int, kind: str, items: list):
-    """Worker entry of both commands' savers: the tensors of ``items`` lie in the shared block (the GPU copied them there).
-    ``kind == "features"``: item = (byte offset, (N, D), index, file, model_name, patch_size, shape, out path) -> the reference's
-    feature dict (extract/extract.py:98-110: ``k`` [1, N, D] f32, ``indices`` a 0-dim int64 tensor, ...).
-    ``kind == "eigs"``: item = (offset of the [K, N] f32 eigenvectors, offset of the [K] f32 eigenvalues, K, N, out path) ->
-    ``{"eigenvalues", "eigenvectors"}`` (:235,243-244).  Returns the number of files written."""
+def save_chunk(block_path: str, block_size: int, items: list):
+    """Worker entry of ``extract_features``' savers: the features of ``items`` lie in the shared block (the GPU copied them
+    there).  Item = (byte offset, (N, D), index, file, model_name, patch_size, shape, out path) -> the reference's feature
+    dict (extract/extract.py:98-110: ``k`` [1, N, D] f32, ``indices`` a 0-dim int64 tensor, ...).  Returns the number of
+    files written."""
     buf = _block(block_path, block_size)
-    for it in items:
-        if kind == "features":
-            off, (n, d), index, file, model_name, patch_size, shape, out = it
-            k = np.frombuffer(buf, dtype=np.float32, count=n * d, offset=off).reshape(1, n, d)
-            write_pth(out, {"k": TensorOut(k), "indices": TensorOut(np.array(index, dtype=np.int64)), "file": file,
-                            "id": os.path.splitext(os.path.basename(file))[0], "model_name": model_name,
-                            "patch_size": int(patch_size), "shape": tuple(int(v) for v in shape)})
-        elif kind == "eigs":
-            voff, eoff, kk, n, out = it
-            vec = np.frombuffer(buf, dtype=np.float32, count=kk * n, offset=voff).reshape(kk, n)
-            val = np.frombuffer(buf, dtype=np.float32, count=kk, offset=eoff)
-            write_pth(out, {"eigenvalues": TensorOut(val), "eigenvectors": TensorOut(vec)})
-        else:
-            raise ValueError(kind)
+    for off, (n, d), index, file, model_name, patch_size, shape, out in items:
+        k = np.frombuffer(buf, dtype=np.float32, count=n * d, offset=off).reshape(1, n, d)
+        write_pth(out, {"k": TensorOut(k), "indices": TensorOut(np.array(index, dtype=np.int64)), "file": file,
+                        "id": os.path.splitext(os.path.basename(file))[0], "model_name": model_name,
+                        "patch_size": int(patch_size), "shape": tuple(int(v) for v in shape)})
     return len(items)
 
 

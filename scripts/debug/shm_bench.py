@@ -50,13 +50,13 @@ t0 = time.perf_counter()
 for _ in range(50): a = pthfast.decode_rgb("/tmp/a.jpg")
 print(f"decode_rgb: {(time.perf_counter() - t0) / 50 * 1e3:.2f} ms per 480x480 JPEG q95")
 for cnt in (10, 18, 50):
-    t0 = time.perf_counter(); blk = extract._ShmBlocks(cnt, 24 << 20); [blk.add() for _ in range(cnt)]; dt = time.perf_counter() - t0
-    print(f"_ShmBlocks({cnt} x 24 MiB): {dt * 1e3:.0f} ms, is_pinned={blk.tensors[0].is_pinned()}")
-    if cnt != 50: blk.close()
-r = pthfast.decode_chunk(blk.paths[3], blk.size, ["/tmp/a.jpg"] * 16)
+    t0 = time.perf_counter(); blks = [extract._ShmBlock(f"/dev/shm/dss_{os.getpid()}_bench_{i}", 24 << 20) for i in range(cnt)]; dt = time.perf_counter() - t0
+    print(f"{cnt} x _ShmBlock(24 MiB): {dt * 1e3:.0f} ms, is_pinned={blks[0].tensor.is_pinned()}")
+    if cnt != 50: [b.free() for b in blks]
+r = pthfast.decode_chunk(blks[3].path, blks[3].nbytes, ["/tmp/a.jpg"] * 16)
 torch.cuda.synchronize(); t0 = time.perf_counter()
-for off, shape in r:
-    x = blk.tensors[3][off:off + 691200].view(shape).to(dev, non_blocking=True)
+for off, shape, _ in r:
+    x = blks[3].tensor[off:off + 691200].view(shape).to(dev, non_blocking=True)
 t1 = time.perf_counter(); torch.cuda.synchronize()
 print(f"16 H2D out of a filled block: enqueue {(t1 - t0) * 1e3:.2f} ms, done {(time.perf_counter() - t0) * 1e3:.2f} ms")
-blk.close()
+[b.free() for b in blks]

@@ -557,10 +557,11 @@ def test_kmeans_segments_default_seeding_batches_and_adaptive():
         assert idx[np.argmax(frac)] == 0                        # the segment owning most of the border is 0
 
 
-def test_pthfast_reads_feature_files_without_torch_semantics_lost(tmp_path):
+def test_pthfast_reads_feature_files_into_offset_shape_meta_entries(tmp_path):
     """The torch-free reader of the extract_eigs loader processes against torch.load on the reference's feature schema
     (extract/extract.py:98-110), including half features, the strided qkv view a CPU run of the reference saves, a
-    non-float tensor (reported, not mis-read) and a foreign pickled class (reported)."""
+    non-float tensor (reported, not mis-read) and a foreign pickled class (reported).  One entry per file of the chunk, in
+    order: ``(byte offset, shape, meta)``, ``(None, None, reason)`` for a file the parent loads itself."""
     import mmap
     import os
 
@@ -593,12 +594,13 @@ def test_pthfast_reads_feature_files_without_torch_semantics_lost(tmp_path):
     block, size = tmp_path / "block", 1 << 20
     with open(block, "wb") as fh:
         fh.truncate(size)
-    out = pthfast.load_chunk(str(block), size, [f for f, _ in files] + [str(strided), str(foreign)], "k")
-    assert len(out) == 6
+    chunk = [f for f, _ in files] + [str(strided), str(foreign)]
+    out = pthfast.load_chunk(str(block), size, chunk, "k")
+    assert len(out) == len(chunk) == 6
     with open(block, "r+b") as fh:
         m = mmap.mmap(fh.fileno(), size)
     expect_off = 0
-    for (f, k), (meta, off, shape) in zip(files, out[:4]):
+    for (f, k), (off, shape, meta) in zip(files, out[:4]):
         assert off == expect_off and shape == tuple(k.shape[1:])
         got = np.frombuffer(m, dtype=np.float32, count=k.numel(), offset=off).reshape(shape)
         assert np.array_equal(got, k[0].float().numpy())
@@ -606,15 +608,15 @@ def test_pthfast_reads_feature_files_without_torch_semantics_lost(tmp_path):
         assert meta == {"indices": int(ref["indices"]), "file": ref["file"], "id": ref["id"], "model_name": ref["model_name"],
                         "patch_size": 16, "shape": tuple(ref["shape"])}
         expect_off += 4 * k.numel()
-    assert out[4][0] is None and out[4][1] == str(strided) and "dtype" in out[4][2]
-    assert out[5][0] is None and out[5][1] == str(foreign) and "numpy" in out[5][2]
+    assert chunk[4] == str(strided) and out[4][:2] == (None, None) and "dtype" in out[4][2]   # the parent loads these two
+    assert chunk[5] == str(foreign) and out[5][:2] == (None, None) and "numpy" in out[5][2]   # itself, by position
     # a block too small for the chunk: the overflow is reported per file, nothing is written past the end
     small = pthfast.load_chunk(str(block), 4 * 48 * 384 + 16, [files[0][0], files[1][0]], "k")
-    assert small[0][0] is not None and small[1][0] is None and "block full" in small[1][2]
+    assert small[0][0] is not None and small[1][:2] == (None, None) and "block full" in small[1][2]
     assert "torch" not in pthfast.__dict__
 
 
-def test_worker_process_pump_runs_without_a_gpu(tmp_path, monkeypatch):
+def test_worker_process_pump_of_offset_shape_meta_entries_runs_without_a_gpu(tmp_path, monkeypatch):
     """`extract._pump_chunks` - torch-free loader processes filling /dev/shm blocks, block recycling in chunk order - with
     the stream events it uses on a GPU replaced by no-ops: every file's feature rows come back intact, in order, through
     fewer blocks than there are chunks."""
@@ -643,8 +645,8 @@ def test_worker_process_pump_runs_without_a_gpu(tmp_path, monkeypatch):
     got, blocks_seen = [], set()
     for entries, block, release in extract._pump_chunks(pthfast.load_chunk, chunks, ("k",), 2, 4 * 4096):
         blocks_seen.add(block.data_ptr())
-        for meta, off, shape in entries:
-            assert meta is not None, (off, shape)
+        for off, shape, meta in entries:
+            assert off is not None and meta is not None, (off, shape)
             rows = block[off:off + 4 * shape[0] * shape[1]].view(torch.float32).view(shape).clone()
             got.append((meta["indices"], rows.numpy()))
         release()
@@ -655,7 +657,7 @@ def test_worker_process_pump_runs_without_a_gpu(tmp_path, monkeypatch):
     assert not [n for n in os.listdir("/dev/shm") if n.startswith(f"dss_{os.getpid()}_")]
 
 
-def test_pthfast_reads_the_reference_written_feature_file(tmp_path, golden_dir):
+def test_pthfast_reads_the_reference_written_feature_file_into_an_offset_shape_meta_entry(tmp_path, golden_dir):
     """tests/golden/ref_feature_file.pth is the file the REFERENCE's extract_features wrote on the CPU (made by
     `oracle/make_golden.py feature_file`): `k` is a strided view of the whole qkv activation.  The torch-free reader
     must return exactly what torch.load returns, and the loader entry point what `_load_features` returns."""
@@ -676,7 +678,7 @@ def test_pthfast_reads_the_reference_written_feature_file(tmp_path, golden_dir):
     block, size = tmp_path / "block", 1 << 16
     with open(block, "wb") as fh:
         fh.truncate(size)
-    (meta, off, shape), = pthfast.load_chunk(str(block), size, [str(path)], "k")
+    (off, shape, meta), = pthfast.load_chunk(str(block), size, [str(path)], "k")
     _, feats = extract._load_features(str(path), "k")
     with open(block, "r+b") as fh:
         m = mmap.mmap(fh.fileno(), size)

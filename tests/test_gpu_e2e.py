@@ -513,6 +513,58 @@ def test_extract_eigs_on_the_reference_written_feature_file(tmp_path, golden_dir
                    d=build_w64(k[0].numpy())[1], ext=ext)
 
 
+class _Injected(Exception):
+    pass
+
+
+@pytest.mark.parametrize("where", ["extract_eigs", "extract_features_main_thread", "extract_features_drain_thread"])
+def test_cli_error_mid_run_leaves_no_workers_blocks_or_threads(tmp_path, monkeypatch, where):
+    """A plain Python exception in the middle of a worker-process run (several chunks of 16 files in flight): when it
+    leaves the command - while the caller still holds its traceback, as pytest.raises does, and without a gc pass - the
+    input generator has been closed, the drain thread stopped and the saver aborted.  No /dev/shm block, worker process or
+    thread of the run is left (the input generator's blocks and workers stayed until a gc pass)."""
+    import multiprocessing
+    import threading
+
+    if extract._shm_free_bytes() < (1 << 30):
+        pytest.skip("/dev/shm too small for the shared blocks of the worker-process path")
+    specs = [(f"p_{i:03d}.png", 300 + i, 96, 128) for i in range(64)]
+    _write_images(tmp_path / "images", specs)
+    (tmp_path / "images.txt").write_text("\n".join(s[0] for s in specs) + "\n")
+    common = ["--images_root", str(tmp_path / "images")]
+    features = ["extract_features", "--images_list", str(tmp_path / "images.txt"), *common, "--output_dir",
+                str(tmp_path / "feat"), "--model_name", "dino_vits16", "--batch_size", "8", "--synthetic_weights", "3"]
+    monkeypatch.setenv("DSS_IO_PROCESSES", "2")
+
+    def fail_on(n, fn):
+        calls = [0]
+
+        def wrapped(*args, **kwargs):
+            calls[0] += 1
+            if calls[0] == n:
+                raise _Injected(f"call {n} of {fn.__name__}")
+            return fn(*args, **kwargs)
+        return wrapped
+
+    if where == "extract_eigs":
+        extract.main(features)
+        monkeypatch.setattr(extract, "_run_eig_batch", fail_on(2, extract._run_eig_batch))
+        argv = ["extract_eigs", *common, "--features_dir", str(tmp_path / "feat"), "--output_dir", str(tmp_path / "eigs"),
+                "--K", "4", "--batch_size", "8"]
+    elif where == "extract_features_main_thread":
+        monkeypatch.setattr(DinoViT, "extract_k", fail_on(3, DinoViT.extract_k))
+        argv = features
+    else:
+        monkeypatch.setattr(extract._FastSaver, "submit_features", fail_on(2, extract._FastSaver.submit_features))
+        argv = features
+    threads, children = set(threading.enumerate()), set(multiprocessing.active_children())
+    with pytest.raises(_Injected):
+        extract.main(argv)
+    assert not list(Path("/dev/shm").glob(f"dss_{os.getpid()}_*")), "shared blocks left behind"
+    assert not [p for p in multiprocessing.active_children() if p not in children], "worker processes left behind"
+    assert not [t for t in threading.enumerate() if t not in threads and t.is_alive()], "threads left behind"
+
+
 def test_cli_two_ranks_shard_round_robin(tmp_path):
     """N>1 on the real kernels: two processes (sharing this box's single GPU; gloo for the barriers) run the two
     CLI stages; together they must produce exactly the single-process outputs, each file written once."""

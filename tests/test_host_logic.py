@@ -286,22 +286,22 @@ def test_dataset_applies_exif_orientation_like_cv2(tmp_path):
     assert np.array_equal(rot.numpy(), np.rot90(arr, k=-1))
 
 
-def test_file_io_worker_processes_round_trip(tmp_path):
+def test_file_io_worker_processes_round_trip_through_the_saver_interface(tmp_path):
     """Large CLI runs hand whole batches to torch-free saver / loader PROCESSES (extract._FastSaver through page-locked
     /dev/shm blocks and the pool's pipe, extract._iter_features): same files as the in-process path, loadable with
-    `torch.load(weights_only=True)`, errors surfaced by wait_slot() / close()."""
+    `torch.load(weights_only=True)`, errors surfaced by close()."""
     k = torch.randn(5, 12, 8)
     items = [(j, 100 + j, f"im_{j}.jpg", "dino_vits16", 16, (1, 3, 48, 64), str(tmp_path / f"im_{j}.pth")) for j in range(5)]
     saver = extract._FastSaver(2)
-    blk = saver.block(1, k.numel() * 4)
-    blk[:k.numel() * 4].view(torch.float32).view(k.shape).copy_(k)
-    saver.submit_features(1, [(j * 12 * 8 * 4, (12, 8), idx, file, m, p, shp, out) for j, idx, file, m, p, shp, out in items], chunk=2)
+    saver.host_buffer((3,), torch.float32)          # a first batch: the features below go through the ring's second slot
+    blk = saver.host_buffer(k.shape, torch.float32)
+    blk.copy_(k)
+    saver.submit_features(blk, items, chunk=2)
     ev, vec = torch.randn(5, 3), torch.randn(5, 3, 12)
     (tmp_path / "e").mkdir()
     saver.submit_batch("eigs", (ev.clone(), vec.clone()), [(j, str(tmp_path / "e" / f"im_{j}.pth"), "laplacian") for j in range(5)])
     labels = (torch.arange(5 * 12).reshape(5, 12) % 7).to(torch.uint8)
     saver.submit_batch("png", (labels,), [(j, str(tmp_path / "e" / f"im_{j}.png"), 3, 4) for j in range(5)])
-    saver.wait_slot(1)
     saver.close()
     from PIL import Image
     for j in range(5):
@@ -319,7 +319,7 @@ def test_file_io_worker_processes_round_trip(tmp_path):
     # the small-run path (threads, torch.save) writes the same dicts - including the 'affinity' branch's numpy eigenvalues
     small = extract._AsyncSaver()
     (tmp_path / "s").mkdir()
-    small.submit_batch("features", (k,), [(*it[:6], str(tmp_path / "s" / f"im_{it[0]}.pth")) for it in items])
+    small.submit_features(k, [(*it[:6], str(tmp_path / "s" / f"im_{it[0]}.pth")) for it in items])
     small.submit_batch("eigs", (ev, vec), [(0, str(tmp_path / "s" / "aff.pth"), "affinity")])
     small.close()
     for j in range(5):
@@ -335,13 +335,12 @@ def test_file_io_worker_processes_round_trip(tmp_path):
     assert set(got) == set(ref) == {f"im_{j}" for j in range(5)} | {"odd"}
     assert all(torch.equal(got[i], ref[i]) for i in got) and got["odd"].shape == (7, 8)
     bad = extract._FastSaver(1)
-    bad.block(0, 64)
-    bad.submit_features(0, [(0, (2, 2), 0, "x.jpg", "m", 16, (1, 3, 4, 4), str(tmp_path / "no_dir" / "x.pth"))])
+    bad.submit_features(bad.host_buffer((1, 2, 2), torch.float32), [(0, 0, "x.jpg", "m", 16, (1, 3, 4, 4), str(tmp_path / "no_dir" / "x.pth"))])
     with pytest.raises(Exception):
         bad.close()
     # a run that FAILS gives its /dev/shm ring back at once (the blocks used to wait for the 6 h stale sweep) ...
     dead = extract._FastSaver(1)
-    dead.block(0, 4096), dead.block(3, 8192)
+    dead.host_buffer((1024,), torch.float32), dead.host_buffer((2048,), torch.float32)
     mine = lambda: [n for n in os.listdir("/dev/shm") if n.startswith(f"dss_{dead.tag}_")]
     assert len(mine()) == 2
     dead.abort()
@@ -363,6 +362,17 @@ def test_file_io_worker_processes_round_trip(tmp_path):
             pthfast._BLOCKS.pop(path, None)
             if os.path.exists(path):
                 os.unlink(path)
+
+
+def test_process_saver_makes_no_block_after_abort():
+    """A drain thread that is still running when its run fails must not create a ring block after the abort(): nothing
+    would unlink it."""
+    saver = extract._FastSaver(1)
+    saver.host_buffer((1024,), torch.float32)
+    saver.abort()
+    with pytest.raises(RuntimeError):
+        saver.host_buffer((1024,), torch.float32)
+    assert not [n for n in os.listdir("/dev/shm") if n.startswith(f"dss_{saver.tag}_")]
 
 
 def test_bucket_batch_is_per_shape_and_inside_the_kernels_row_limits():
